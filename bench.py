@@ -15,13 +15,19 @@ the job is completed inside the timed region (multi-GPU: the RCCL all-reduce of 
 the eigensolve and the device->host copy of the components), so ``value`` is whole-job throughput and
 ``ms_per_step * steps`` is the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode exact|faithful]     (N > 1: re-executes itself under the launcher below)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode exact|faithful] [--dump-outputs DIR]
+                                                                      (N > 1: runs itself under the launcher below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 With N ranks the job is the 8-GPU config in miniature (BASELINE cfg4 layout): ONE z stream for n = N x K x 50 000
 samples, rank r owns the contiguous block range ``distributed.shard_range`` gives it and generates only those z
 batches (weak scaling: the per-GPU work is fixed).  Rank 0 prints ONE JSON line (plus notes on stderr).
+
+``--dump-outputs DIR``: rank 0 writes what the timed job returned to its caller - ``get_components()`` (components,
+stdev, explained-variance ratio) and the transformer's ``mean_`` - as ``DIR/<name>.npy`` (float32 / float64).  The
+inputs are seeded (random-init model under ``torch.manual_seed(0)``, the reference's z stream), so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import contextlib
@@ -297,6 +303,26 @@ def launcher_command(argv, n_ranks, port=None):
             "--master-addr", "127.0.0.1", "--master-port", str(int(port)), os.path.abspath(__file__), *argv]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write ``{name: array}`` as ``out_dir/<name>.npy``: float64 stays float64, every other dtype is stored as float32
+    (the timed job's outputs are tiny - 80 x 512 components and three 80- / 512-vectors - far below the 64 MB cap).
+    Returns the paths written."""
+    conv = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+            for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"outputs of {total} bytes exceed the {DUMP_MAX_BYTES}-byte dump cap")
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for k, a in conv.items():
+        paths.append(os.path.join(out_dir, f"{k}.npy"))
+        np.save(paths[-1], a)
+    return paths
+
+
 def main():
     global T_BENCH0
     T_BENCH0 = time.perf_counter()
@@ -324,15 +350,20 @@ def main():
                          "at ~24 us per sample through the f32-MFMA GEMM)")
     ap.add_argument("--wide-cpu-threads", type=int, default=32, help="BLAS threads of that baseline")
     ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed job's results (components, stdev, explained-variance ratio, mean) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` (how the driver's 1-GPU line is invoked, with N > 1): start the N ranks ourselves
+        # `python bench.py --gpus N` (how the driver's 1-GPU line is invoked, with N > 1): start the N ranks ourselves, as a
+        # child process (this one never touches the device) whose exit code becomes ours
+        import subprocess
         cmd = launcher_command(sys.argv[1:], args.gpus)
-        log("bench.py: --gpus %d without a launcher: exec %s" % (args.gpus, " ".join(cmd)))
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        log("bench.py: --gpus %d without a launcher: running %s" % (args.gpus, " ".join(cmd)))
+        env = dict(os.environ)
+        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush()
-        os.execv(cmd[0], cmd)
+        sys.exit(subprocess.call(cmd, env=env))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -372,6 +403,7 @@ def main():
     ar_events = []
 
     def run(est, nsteps, finish=True):
+        """``nsteps`` steps of the job into ``est``; with ``finish``, returns what ``get_components()`` returned."""
         if est.mode == "exact":
             # (the product's W-space loop does the same: decomposition._fit_blocks hands over views of the resident
             #  latent array, the estimator contracts them in launches of 131 072 rows)
@@ -389,7 +421,7 @@ def main():
                 gdist.allreduce_estimator(est, d=D)
                 e1.record()
                 ar_events.extend((e0, e1))
-            est.get_components()           # eigensolve (exact mode) + D2H of the results
+            return est.get_components()    # eigensolve (exact mode) + D2H of the results
 
     # ---- warm-up (untimed) ------------------------------------------------------------------
     est = IPCAEstimator(K_COMP, args.mode)
@@ -400,7 +432,7 @@ def main():
     # ---- timed region ------------------------------------------------------------------------
     barrier()
     t0 = time.perf_counter()
-    run(est, K)
+    timed_result = run(est, K)
     barrier()
     dt = time.perf_counter() - t0
     dt_local = dt
@@ -424,6 +456,11 @@ def main():
                          "all-reduce, re-centring, packed scatter all-reduce, import); T_sample_s is outside it"}
     if rank == 0 and os.environ.get("GS_BENCH_DUMP"):       # test hook: the components the timed job produced
         np.save(os.environ["GS_BENCH_DUMP"], est.get_components()[0])
+    if rank == 0 and args.dump_outputs:
+        comp_t, stdev_t, ratio_t = timed_result
+        paths = dump_outputs(args.dump_outputs, {"components": comp_t, "stdev": stdev_t,
+                                                 "explained_variance_ratio": ratio_t, "mean": est.transformer.mean_})
+        log(f"bench.py: timed job's outputs written: {', '.join(paths)}")
 
     # ---- split of the job: update loop vs finalize ----------------------------------------------
     est2 = IPCAEstimator(K_COMP, args.mode)
@@ -851,7 +888,7 @@ def main():
 
     # ---- the wide shapes' CPU baselines, LAST and alone on the host (beside the GPU legs they ran 2-5x slower and slowed
     #      the host-bound GPU legs down in turn): scikit-learn's IncrementalPCA.partial_fit - the reference's arithmetic,
-    #      /root/reference/estimators.py:68-76 - on CPU-seeded blocks of the same synthetic workload, first block + up to
+    #      the reference's estimators.py:68-76 - on CPU-seeded blocks of the same synthetic workload, first block + up to
     #      `--wide-cpu-blocks - 1` steady-state blocks (SURVEY.md 8d asks for >= 5) while the run's budget lasts; the n = 1e6
     #      job (500 blocks) is extrapolated.  The same blocks then go through the device estimator for the cosine ----------
     if extras and not args.no_wide and not args.no_cpu_baseline:

@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures under tests/golden/ from the REAL reference.
 
-Run in the build container only (needs /root/reference, which does not exist on
-the GPU box):   python tests/golden/make_golden.py
+Needs a checkout of the reference (harskish/ganspace), given on the command line;
+the tests only read the fixtures it writes:
+    python tests/golden/make_golden.py <reference checkout>
 
 What it imports from the reference (nothing is copied into the repo):
-* ``/root/reference/estimators.py`` -> ``get_estimator('ipca', k, 1.0)``
+* ``<reference>/estimators.py`` -> ``get_estimator('ipca', k, 1.0)``
   (the absent third-party ``fbpca`` module is stubbed); the
   arithmetic it delegates to is scikit-learn's ``IncrementalPCA`` installed in
   this image (1.7.2).
-* ``/root/reference/models/stylegan/model.py`` -> ``G_mapping`` (the only
+* ``<reference>/models/stylegan/model.py`` -> ``G_mapping`` (the only
   in-tree 8 x (512->512) mapping MLP) with explicitly seeded weights.
 
 Inputs are *not* stored: each fixture records the generator parameters and
@@ -27,7 +28,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import inputs as gin  # noqa: E402
 
-REF = "/root/reference"
+REF = None            # the reference checkout (command line)
 
 
 def load_reference_estimators():
@@ -71,6 +72,10 @@ def run_ipca_case(est_mod, case):
 
 
 def main():
+    global REF
+    if len(sys.argv) != 2 or not os.path.isfile(os.path.join(sys.argv[1], "estimators.py")):
+        raise SystemExit("usage: python tests/golden/make_golden.py <reference checkout>")
+    REF = sys.argv[1]
     est_mod = load_reference_estimators()
     import sklearn
     for name, case in gin.IPCA_CASES.items():

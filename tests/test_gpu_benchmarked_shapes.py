@@ -4,7 +4,7 @@ contraction) - not at a miniature of them.
 
 Checker: ``oracle/smallside_torch.py`` (float64 restatement of sklearn's recurrence on the r x r side, pinned to the
 SVD-form oracle in tests/test_oracle.py), and for d = 32 768 scikit-learn's ``IncrementalPCA`` itself, configured as
-``/root/reference/estimators.py:59`` does, on the first six blocks."""
+the reference's ``estimators.py:59`` does, on the first six blocks."""
 import numpy as np
 import pytest
 

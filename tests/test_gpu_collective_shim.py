@@ -4,7 +4,7 @@ lets P estimator handles on the box's single GPU go through the entry's whole P 
 all-reduce, the Chan re-centring of the local scatter about the global mean (also for a rank that saw no samples), the
 scatter all-reduce and import; for the faithful estimators the all-gather layout and ``gs_ipca_lowrank_merge``.  RCCL
 itself refuses two ranks on one device (the only N > 1 RCCL run is the driver's 8-GPU bench), so this is the one place
-where that arithmetic runs before then.  Reference loop being sharded: ``/root/reference/decomposition.py:245-267``."""
+where that arithmetic runs before then.  Reference loop being sharded: the reference's ``decomposition.py:245-267``."""
 import os
 import subprocess
 import sys
@@ -26,7 +26,8 @@ def shim():
     so = os.path.join(SHIM_DIR, "libfake_rccl.so")
     src = os.path.join(SHIM_DIR, "fake_rccl.cpp")
     if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
-        subprocess.run(["/opt/rocm/bin/hipcc", "-w", "-O2", "-shared", "-fPIC", src, "-o", so], check=True)
+        from ganspace_amd import _build
+        subprocess.run([_build._hipcc(), "-w", "-O2", "-shared", "-fPIC", src, "-o", so], check=True)
     return so
 
 

@@ -176,3 +176,25 @@ def test_bench_launches_its_own_ranks(tmp_path):
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["value"] > 0
     assert len(line["multi_gpu"]["per_rank"]) == 2
+
+
+def test_bench_dump_outputs_are_the_timed_jobs_results(tmp_path):
+    """``bench.py --dump-outputs DIR`` (one process, no launcher): the timed job's ``get_components()`` and ``mean_`` as
+    ``DIR/<name>.npy``, float32 components and float64 statistics; the components are those the ``GS_BENCH_DUMP`` hook
+    saves from the same estimator, and ``--steps`` sets the timed job (steps x 50 000 samples)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(GS_BENCH_DUMP=str(tmp_path / "hook.npy"), PYTHONPATH=ROOT + os.pathsep + env.get("PYTHONPATH", ""))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--no-extras", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, f"--- stdout ---\n{r.stdout[-3000:]}\n--- stderr ---\n{r.stderr[-6000:]}"
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and "n=150000" in line["config"]["workload"]
+    assert sorted(os.listdir(out)) == ["components.npy", "explained_variance_ratio.npy", "mean.npy", "stdev.npy"]
+    got = {name[:-4]: np.load(out / name) for name in os.listdir(out)}
+    assert got["components"].dtype == np.float32 and got["components"].shape == (80, 512)
+    for name, shape in (("stdev", (80,)), ("explained_variance_ratio", (80,)), ("mean", (512,))):
+        assert got[name].dtype == np.float64 and got[name].shape == shape, name
+    assert all(np.isfinite(a).all() for a in got.values())
+    np.testing.assert_array_equal(got["components"], np.load(tmp_path / "hook.npy"))
+    assert (np.diff(got["stdev"]) <= 0).all() and 0 < got["explained_variance_ratio"].sum() <= 1 + 1e-9

@@ -369,6 +369,30 @@ def test_bench_builds_the_launcher_line_for_multi_gpu_runs():
     assert 1024 <= int(auto[auto.index("--master-port") + 1]) <= 65535
 
 
+def test_bench_output_dump_writes_float32_and_float64_npy(tmp_path):
+    """``bench.py --dump-outputs DIR`` writer: one ``DIR/<name>.npy`` per array, float64 kept, every other dtype stored as
+    float32, values unchanged; more than 64 MB in all is refused before anything is written."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rs = np.random.RandomState(0)
+    arrays = {"components": rs.standard_normal((80, 512)).astype(np.float32), "stdev": rs.rand(80),
+              "counts": np.arange(5, dtype=np.int64)}
+    out = tmp_path / "dump"
+    paths = bench.dump_outputs(str(out), arrays)
+    assert sorted(os.path.basename(p) for p in paths) == ["components.npy", "counts.npy", "stdev.npy"]
+    for name, want in arrays.items():
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == (np.float64 if want.dtype == np.float64 else np.float32) and got.shape == want.shape
+        np.testing.assert_array_equal(got, want)
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((bench.DUMP_MAX_BYTES // 8) + 1, np.float64)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_mt19937_jump_polynomials_reach_the_states_numpy_reaches():
     """ganspace_amd/data/mt19937_jump_L2048.npz (tools/make_mt_jump.py): polynomial i is x^(i * 2048 * 624) mod phi, and the
     state block of a stream at that offset is the XOR of the windows words[k : k + 624] of its first 33 blocks over the set
